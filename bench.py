@@ -21,6 +21,16 @@ rate are reported alongside in config.
 
 Driver contract: `python bench.py --gpus N --steps K --warmup W`; for
 N>1 launched under torchrun, one rank per GPU over RCCL.
+
+A plain run does only what the headline needs: K timed (profiled) steps,
+and a baseline phase capped at PLAIN_BASELINE_STEPS steps whose CPU and
+wall time are scaled to K, and a settle that ends as soon as the agent
+daemon's startup burst is over. `--full` runs the baseline over all K
+steps, which is what the slowdown % and baseline ms/step in config
+deserve, and settles for a fixed 8 s.
+`--dump-outputs DIR` writes what the last timed step returned (loss and a
+fixed, seeded sample of the logits) as DIR/<name>.npy for comparing two
+builds output for output.
 """
 
 import argparse
@@ -93,12 +103,41 @@ def build_model(device, dtype, model_name):
     return model
 
 
+# Baseline steps of a plain (non --full) run.
+PLAIN_BASELINE_STEPS = 10
+# Logit elements kept by --dump-outputs (4 MB as float32).
+DUMP_LOGIT_SAMPLES = 1 << 20
+
+
 def run_steps(model, opt, batch, n_steps):
+    """Run n_steps training steps; returns the last step's model output."""
+    out = None
     for _ in range(n_steps):
         out = model(input_ids=batch, labels=batch)
         out.loss.backward()
         opt.step()
         opt.zero_grad(set_to_none=True)
+    return out
+
+
+def dump_outputs(out, directory):
+    """Write the last timed step's loss and a seeded sample of its logits
+    as float32 .npy files. The sample positions depend only on the logits'
+    size, so two builds run with the same arguments dump the same ones."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    loss = out.loss.detach().float().reshape(1).cpu().numpy()
+    np.save(os.path.join(directory, "loss.npy"), loss)
+    logits = out.logits.detach().reshape(-1)
+    n = logits.numel()
+    if n > DUMP_LOGIT_SAMPLES:
+        gen = torch.Generator(device="cpu")
+        gen.manual_seed(20240517)
+        idx = torch.randint(0, n, (DUMP_LOGIT_SAMPLES,), generator=gen)
+        logits = logits[idx.sort().values.to(logits.device)]
+    np.save(os.path.join(directory, "logits_sample.npy"),
+            logits.float().cpu().numpy())
 
 
 def proc_cpu_seconds(pid: int) -> float:
@@ -136,6 +175,26 @@ class AgentDaemon:
         except (OSError, ValueError):
             return 0.0
 
+    def wait_settled(self, max_seconds: float, min_seconds: float = 3.0,
+                     window: float = 0.5, busy_core_share: float = 0.3,
+                     calm_windows: int = 3) -> None:
+        """Sleep until the daemon's startup burst (imports, perf attach,
+        ring discovery) is over: `calm_windows` consecutive windows in
+        which it used under `busy_core_share` of one core, no sooner than
+        `min_seconds` and never longer than `max_seconds`."""
+        t0 = time.monotonic()
+        last = self.cpu_seconds()
+        calm = 0
+        while True:
+            elapsed = time.monotonic() - t0
+            if elapsed >= max_seconds or \
+                    (elapsed >= min_seconds and calm >= calm_windows):
+                return
+            time.sleep(min(window, max_seconds - elapsed))
+            now = self.cpu_seconds()
+            calm = calm + 1 if now - last < busy_core_share * window else 0
+            last = now
+
     def rss_mb(self) -> float:
         try:
             with open(f"/proc/{self.proc.pid}/statm") as fh:
@@ -167,6 +226,13 @@ def main():
     ap.add_argument("--model", default=None,
                     help="llama3-8b (default on GPU) or tiny")
     ap.add_argument("--device", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="baseline phase over all --steps steps (exact "
+                         "slowdown %% and baseline ms/step) instead of a "
+                         "short scaled one")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to "
+                         "DIR/<name>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -213,14 +279,19 @@ def main():
     barrier()
 
     # ---- phase A: baseline, no profiling anywhere ----
+    # Scaled to args.steps so it compares with phase B step for step.
+    base_steps = args.steps if args.full else \
+        min(args.steps, PLAIN_BASELINE_STEPS)
+    base_scale = args.steps / base_steps if base_steps else 0.0
     ru0 = resource.getrusage(resource.RUSAGE_SELF)
     t0 = time.perf_counter()
-    run_steps(model, opt, batch, args.steps)
+    run_steps(model, opt, batch, base_steps)
     sync()
     barrier()
-    t_base = time.perf_counter() - t0
+    t_base = (time.perf_counter() - t0) * base_scale
     ru1 = resource.getrusage(resource.RUSAGE_SELF)
-    cpu_base = (ru1.ru_utime + ru1.ru_stime) - (ru0.ru_utime + ru0.ru_stime)
+    cpu_base = ((ru1.ru_utime + ru1.ru_stime) -
+                (ru0.ru_utime + ru0.ru_stime)) * base_scale
 
     # ---- bring up production-shaped profiling ----
     # One agent daemon on the node (local_rank 0 owns it); every rank
@@ -228,10 +299,18 @@ def main():
     from parca_agent_amd.agent import InProcessToolControl
 
     agent = None
-    out_dir = os.environ.get("PARCA_BENCH_STORE",
-                             os.path.join(REPO, "gpurun_out"))
-    os.makedirs(out_dir, exist_ok=True)
+    # The daemon's profiles and stats file go to PARCA_BENCH_STORE when
+    # set (and stay there); otherwise to a scratch directory that is
+    # removed once the stats are read — the checkout may be read-only.
+    out_dir = os.environ.get("PARCA_BENCH_STORE")
+    scratch_dir = None
     if local_rank == 0:
+        if out_dir:
+            os.makedirs(out_dir, exist_ok=True)
+        else:
+            import tempfile
+
+            out_dir = scratch_dir = tempfile.mkdtemp(prefix="parca_bench_")
         agent = AgentDaemon(os.path.join(out_dir, "bench_profiles"),
                             os.path.join(out_dir, "agent_stats.json"))
     tool = None
@@ -245,8 +324,15 @@ def main():
     # Settle: agent attach, ring discovery and one-time .eh_frame
     # stack-delta table builds (libtorch-scale) happen off the clock —
     # they are startup costs, not steady-state overhead.
-    time.sleep(float(os.environ.get("PARCA_BENCH_SETTLE",
-                                    "8" if agent is not None else "0.5")))
+    # --full (and an explicit PARCA_BENCH_SETTLE) sleeps a fixed time; a
+    # plain run watches the daemon's CPU and moves on once it has calmed
+    # down, within that same limit.
+    settle = os.environ.get("PARCA_BENCH_SETTLE")
+    if settle is not None or args.full or agent is None:
+        time.sleep(float(settle if settle is not None else
+                         "8" if agent is not None else "0.5"))
+    else:
+        agent.wait_settled(max_seconds=8.0)
     run_steps(model, opt, batch, 1)
     sync()
     barrier()
@@ -255,7 +341,7 @@ def main():
     agent_cpu0 = agent.cpu_seconds() if agent is not None else 0.0
     ru2 = resource.getrusage(resource.RUSAGE_SELF)
     t1 = time.perf_counter()
-    run_steps(model, opt, batch, args.steps)
+    last_out = run_steps(model, opt, batch, args.steps)
     sync()
     barrier()
     t_prof = time.perf_counter() - t1
@@ -270,6 +356,14 @@ def main():
         {"written": 0, "dropped": 0, "launch_stacks": 0}
     time.sleep(1.0)  # let the agent drain the tail before stopping it
     agent_stats = agent.stop() if agent is not None else {}
+    if scratch_dir is not None:
+        import shutil
+
+        shutil.rmtree(scratch_dir, ignore_errors=True)
+
+    if args.dump_outputs and rank == 0 and last_out is not None:
+        dump_outputs(last_out, args.dump_outputs)
+    del last_out
 
     # Per-rank in-workload tool cost; agent cost counted once per node.
     tool_cpu = max(cpu_prof - cpu_base, 0.0)
@@ -328,6 +422,7 @@ def main():
                 "slowdown_pct": round(slowdown_pct, 4),
                 "dropped_sample_pct": round(dropped_pct, 6),
                 "baseline_ms_per_step": round(1000.0 * t_base / args.steps, 3),
+                "baseline_steps": base_steps,
                 "agent_cpu_seconds": round(agent_cpu, 4),
                 "agent_rss_mb": round(agent_rss_mb, 1),
                 "tool_cpu_seconds": round(tool_cpu_sum, 4),

@@ -227,6 +227,12 @@ class PerfSampler {
       }
 
       int fd = perf_event_open(&attr, target_pid_, cpu, -1, PERF_FLAG_FD_CLOEXEC);
+      if (fd < 0 && (errno == EACCES || errno == EPERM) && target_pid_ >= 0) {
+        // Unprivileged at perf_event_paranoid=2: a per-task event on one of
+        // the caller's own processes is still allowed, user space only.
+        attr.exclude_kernel = 1;
+        fd = perf_event_open(&attr, target_pid_, cpu, -1, PERF_FLAG_FD_CLOEXEC);
+      }
       if (fd < 0) {
         if (errno == EACCES || errno == EPERM)
           throw std::runtime_error(

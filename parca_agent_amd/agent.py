@@ -255,7 +255,17 @@ class Agent:
         if self._prob_controller is not None:
             self._prob_controller.start()  # owns the CPU sampler lifecycle
         elif self.cpu_service is not None:
-            self.cpu_service.start()
+            try:
+                self.cpu_service.start()
+            except RuntimeError as e:
+                # System-wide perf events need root/CAP_PERFMON. Without
+                # them the GPU side (shm rings written by the in-process
+                # tool) still works, so run GPU-only and say so loudly.
+                if "permission denied" not in str(e):
+                    raise
+                log.warning("CPU sampling disabled, GPU profiling only: %s", e)
+                self.cpu_service.stop()
+                self.cpu_service = None
         if self.offcpu_service is not None:
             self.offcpu_service.start()
         if self.gpu_service is not None:

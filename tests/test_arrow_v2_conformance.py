@@ -2,14 +2,15 @@
 
 VERDICT.md missing#4/weak#2: round-1 validated our v2 bytes only
 against pyarrow and an in-repo fake server built from the same codecs.
-A real Parca server cannot run in this offline image, so this test
-breaks the closed loop differently: the EXPECTED schema is derived
-from /root/reference/reporter/arrow_v2.go itself —
+A real Parca server cannot run offline, so this test breaks the closed
+loop differently: the EXPECTED schema comes from the reference agent's
+reporter/arrow_v2.go —
 
-  * field ORDER is regex-extracted from ArrowSamplesFieldV2's
-    ``fields[N] = <Var>`` assignments and each Var's ``Name:`` literal
-    (arrow_v2.go:581-604), so a drift in the reference ordering breaks
-    this test, not just our transcription;
+  * field ORDER and the schema-version metadata pair are recorded in
+    tests/golden/arrow_v2_reference_schema.json, extracted from
+    ArrowSamplesFieldV2's ``fields[N] = <Var>`` assignments, each Var's
+    ``Name:`` literal (arrow_v2.go:581-604) and the MetadataSchemaVersion
+    constants, so the suite needs no reference checkout to run;
   * field TYPES are transcribed here construct-by-construct with
     file:line citations and compared against the schema pyarrow (an
     independent C++ Arrow implementation) re-parses from our actual
@@ -22,10 +23,10 @@ accepting the bytes end-to-end (BASELINE config 5); that remains
 documented as unproven in docs/.
 """
 
-import re
+import json
+import os
 
 import pyarrow as pa
-import pytest
 
 from parca_agent_amd.model import Frame, FrameType, MappingFile, Trace
 from parca_agent_amd.reporter.arrow_v2 import (
@@ -33,16 +34,13 @@ from parca_agent_amd.reporter.arrow_v2 import (
     serialize_record,
 )
 
-REF = "/root/reference/reporter/arrow_v2.go"
-REF_ARROW = "/root/reference/reporter/arrow.go"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                      "golden", "arrow_v2_reference_schema.json")
 
 
-def _ref_source():
-    try:
-        with open(REF) as fh:
-            return fh.read()
-    except OSError:
-        pytest.skip("reference source unavailable")
+def _ref_schema():
+    with open(GOLDEN) as fh:
+        return json.load(fh)
 
 
 def _emit_batch():
@@ -71,25 +69,7 @@ def _emit_batch():
 
 
 def test_field_order_matches_reference_source():
-    src = _ref_source()
-    body = src.split("func ArrowSamplesFieldV2", 1)[1]
-    body = body.split("return fields", 1)[0]
-    assigns = re.findall(
-        r"fields\[(\d+)\]\s*=\s*(?:arrow\.Field\{\s*Name:\s*\"(\w+)\""
-        r"|(\w+))", body)
-    order = {}
-    var_names = {}
-    for m in re.finditer(
-            r"(\w+)\s*=\s*arrow\.Field\{\s*Name:\s*\"(\w+)\"",
-            src + open(REF_ARROW).read()):
-        var_names[m.group(1)] = m.group(2)
-    for idx, inline, var in assigns:
-        if inline:
-            order[int(idx)] = inline
-        else:
-            assert var in var_names, f"unresolved field var {var}"
-            order[int(idx)] = var_names[var]
-    expected = [order[i] for i in sorted(order)]
+    expected = _ref_schema()["field_order"]
     assert len(expected) == 13
 
     _batch, schema = _emit_batch()
@@ -162,10 +142,8 @@ def test_types_match_reference_definitions():
 
 
 def test_metadata_key_value_from_reference():
-    src = _ref_source() + open(REF_ARROW).read()
-    key = re.search(r'MetadataSchemaVersion\s*=\s*"([^"]+)"', src).group(1)
-    val = re.search(r'MetadataSchemaVersionV2\s*=\s*"([^"]+)"',
-                    src).group(1)
+    ref = _ref_schema()
+    key, val = ref["metadata_key"], ref["metadata_value"]
     _batch, schema = _emit_batch()
     assert schema.metadata[key.encode()] == val.encode()
 

@@ -5,8 +5,10 @@ clients, containermetadata.go:250-296, 353-470, 481-525)."""
 import http.server
 import json
 import os
+import shutil
 import socket
 import socketserver
+import tempfile
 import threading
 import time
 
@@ -192,8 +194,11 @@ class FakeDockerHandler(http.server.BaseHTTPRequestHandler):
             self.end_headers()
 
 
-def test_docker_client_over_unix_socket(tmp_path):
-    sock_path = str(tmp_path / "docker.sock")
+def test_docker_client_over_unix_socket():
+    # AF_UNIX paths are capped at 107 bytes; pytest's tmp_path can be
+    # deeper than that, so bind under a short directory of our own.
+    sock_dir = tempfile.mkdtemp(prefix="dk", dir="/tmp")
+    sock_path = os.path.join(sock_dir, "docker.sock")
 
     class UnixHTTPServer(socketserver.ThreadingUnixStreamServer):
         def get_request(self):
@@ -214,6 +219,8 @@ def test_docker_client_over_unix_socket(tmp_path):
         assert c.container_labels("f" * 64) == {}
     finally:
         srv.shutdown()
+        srv.server_close()
+        shutil.rmtree(sock_dir, ignore_errors=True)
 
 
 def test_reference_kubernetes_config_workflow(apiserver, monkeypatch):

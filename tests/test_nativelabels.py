@@ -20,6 +20,10 @@ perf = pytest.mark.skipif(
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 NSLOTS, MAXL, KLEN, VLEN = 512, 8, 32, 64
+# Synthetic tables stand in for processes that do not exist: the kernel
+# never hands out a pid above 2**22, so the reader's owner check (table
+# owner vs. /proc/<pid> owner) cannot trip over an unrelated live process.
+GONE = 1 << 22
 SLOT_SIZE = SLOT_HEAD.size + MAXL * (KLEN + VLEN)
 
 
@@ -44,24 +48,24 @@ def _reader_for(tmp_path, pid, table_bytes):
 
 def test_reader_basic(tmp_path):
     tid = 4242
-    r = _reader_for(tmp_path, 100, _mk_table({
+    r = _reader_for(tmp_path, GONE + 100, _mk_table({
         tid % NSLOTS: (tid, 2, [("service", "billing"),
                                 ("endpoint", "/checkout")])}))
-    assert r.labels_for(100, tid) == (("service", "billing"),
+    assert r.labels_for(GONE + 100, tid) == (("service", "billing"),
                                       ("endpoint", "/checkout"))
-    assert r.labels_for(100, tid + 1) == ()  # other tid: free slot
+    assert r.labels_for(GONE + 100, tid + 1) == ()  # other tid: free slot
     assert r.samples_labeled == 1
 
 
 def test_reader_probing_and_holes(tmp_path):
     # Two tids colliding on the same home slot; second lives one over.
     t1, t2 = 7, 7 + NSLOTS
-    r = _reader_for(tmp_path, 5, _mk_table({
+    r = _reader_for(tmp_path, GONE + 5, _mk_table({
         7: (t1, 0, [("a", "1")]),
         8: (t2, 4, [("b", "2")]),
     }))
-    assert r.labels_for(5, t1) == (("a", "1"),)
-    assert r.labels_for(5, t2) == (("b", "2"),)
+    assert r.labels_for(GONE + 5, t1) == (("a", "1"),)
+    assert r.labels_for(GONE + 5, t2) == (("b", "2"),)
 
     # Deleted label leaves a hole: count=1 but label parked at index 2.
     buf = bytearray(_mk_table({33: (33, 0, [])}))
@@ -70,9 +74,9 @@ def test_reader_probing_and_holes(tmp_path):
     p = off + SLOT_HEAD.size + 2 * (KLEN + VLEN)
     buf[p:p + 4] = b"late"
     buf[p + KLEN:p + KLEN + 2] = b"ok"
-    (tmp_path / "parca_labels_6").write_bytes(bytes(buf))
+    (tmp_path / f"parca_labels_{GONE + 6}").write_bytes(bytes(buf))
     r2 = NativeLabelReader(directory=str(tmp_path))
-    assert r2.labels_for(6, 33) == (("late", "ok"),)
+    assert r2.labels_for(GONE + 6, 33) == (("late", "ok"),)
 
 
 def test_reader_seqlock_and_negative_cache(tmp_path):

@@ -100,7 +100,10 @@ def test_perl_frames_in_profile(busy_perl):
 
     dest = Dest()
     rep = Reporter([dest], cpu_sampling_frequency=97)
-    svc = CPUSamplerService(rep, freq=97, poll_interval=0.05)
+    # Sample the interpreter alone: per-task events on one's own child
+    # need no privilege, system-wide ones need root or CAP_PERFMON.
+    svc = CPUSamplerService(rep, freq=97, poll_interval=0.05,
+                            target_pid=busy_perl.pid)
     svc.perl_unwinder = PerlUnwinder()
     assert svc.perl_unwinder.available
     svc.start()

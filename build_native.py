@@ -99,7 +99,8 @@ def build_gpu(debug: bool = False, force: bool = False) -> Path:
     out = OUT / f"_gpu{EXT_SUFFIX}"
     if not srcs:
         return out
-    if not force and not _needs_build(out, srcs + [CSRC / "rocprof" / "ring.h"]):
+    deps = srcs + [CSRC / "gpu" / "bucketize.h", CSRC / "rocprof" / "ring.h"]
+    if not force and not _needs_build(out, deps):
         return out
     opt = "-O1" if debug else "-O3"
     hipcc = str(ROCM / "bin" / "hipcc")

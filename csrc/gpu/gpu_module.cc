@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include "gpu/bucketize.h"
 #include "rocprof/ring.h"
 
 namespace py = pybind11;
@@ -279,23 +280,40 @@ class TestRingProducer {
 
 // -- device bucketize -----------------------------------------------------
 
-namespace parca_gpu {
-struct BucketizeArgs {
-  const uint64_t* code_object_ids;
-  const uint64_t* offsets;
-  const uint64_t* exec_masks;
-  uint32_t n;
-  const uint64_t* slot_ids;
-  const uint32_t* slot_offsets;
-  uint32_t n_slots;
-  uint32_t bucket_shift;
-  uint32_t total_buckets;
-  uint32_t* histogram;
-  uint64_t* lane_histogram;
-  uint32_t* overflow;
-};
-void launch_bucketize(const BucketizeArgs& args, hipStream_t stream);
-}  // namespace parca_gpu
+// One pass over the PCSample records of a ring batch: the four SoA
+// columns the bucketizer uploads, plus the OR of every flags word (bit 1
+// of it says whether any sample carries issue info). A record is one
+// 64-byte cache line, so pulling the fields out one numpy gather at a
+// time reads the whole batch from memory once per field; at PC-sample
+// rates that host cost, not the kernel, bounds bucketize throughput.
+py::tuple split_pc_samples(py::array samples) {
+  if (samples.ndim() != 1 ||
+      samples.itemsize() != static_cast<py::ssize_t>(sizeof(PCSample)))
+    throw std::invalid_argument("expected a 1-d array of 64-byte PCSample");
+  const py::ssize_t n = samples.shape(0);
+  const py::ssize_t stride = n > 0 ? samples.strides(0) : 0;
+  const uint8_t* base = static_cast<const uint8_t*>(samples.data());
+  py::array_t<uint64_t> co(n), off(n), exec(n);
+  py::array_t<uint32_t> flags(n);
+  uint64_t* co_p = co.mutable_data();
+  uint64_t* off_p = off.mutable_data();
+  uint64_t* exec_p = exec.mutable_data();
+  uint32_t* flags_p = flags.mutable_data();
+  uint32_t flags_or = 0;
+  {
+    py::gil_scoped_release rel;
+    for (py::ssize_t i = 0; i < n; ++i) {
+      PCSample s;  // records sit 8-byte aligned behind the batch header
+      memcpy(&s, base + i * stride, sizeof(s));
+      co_p[i] = s.code_object_id;
+      off_p[i] = s.code_object_offset;
+      exec_p[i] = s.exec_mask;
+      flags_p[i] = s.flags;
+      flags_or |= s.flags;
+    }
+  }
+  return py::make_tuple(co, off, exec, flags, flags_or);
+}
 
 class DeviceBucketizer {
  public:
@@ -335,7 +353,9 @@ class DeviceBucketizer {
                     static_cast<void*>(d_hist_),
                     static_cast<void*>(d_lane_hist_),
                     static_cast<void*>(d_overflow_), static_cast<void*>(d_co_),
-                    static_cast<void*>(d_off_), static_cast<void*>(d_exec_)})
+                    static_cast<void*>(d_off_), static_cast<void*>(d_exec_),
+                    static_cast<void*>(d_flags_),
+                    static_cast<void*>(d_stall_)})
       if (p) (void)hipFree(p);
     if (stream_) (void)hipStreamDestroy(stream_);
   }
@@ -347,6 +367,8 @@ class DeviceBucketizer {
     HIP_CHECK(hipMemsetAsync(d_lane_hist_, 0,
                              total_buckets_ * sizeof(uint64_t), stream_));
     HIP_CHECK(hipMemsetAsync(d_overflow_, 0, 2 * sizeof(uint32_t), stream_));
+    if (d_stall_ != nullptr)
+      HIP_CHECK(hipMemsetAsync(d_stall_, 0, stall_bytes(), stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
   }
 
@@ -355,6 +377,75 @@ class DeviceBucketizer {
   void accumulate(py::array_t<uint64_t> code_object_ids,
                   py::array_t<uint64_t> offsets,
                   py::array_t<uint64_t> exec_masks) {
+    accumulate_impl(code_object_ids, offsets, exec_masks, nullptr);
+  }
+
+  // As accumulate(), with the samples' PCSample.flags: the same launch
+  // also fills the per-(bucket, stall column) matrix. The matrix and the
+  // flags staging buffer exist only from the first call on, so a
+  // bucketizer that never sees stochastic samples never allocates them
+  // (64 B per bucket: 256 MiB at the largest layout).
+  void accumulate_flagged(py::array_t<uint64_t> code_object_ids,
+                          py::array_t<uint64_t> offsets,
+                          py::array_t<uint64_t> exec_masks,
+                          py::array_t<uint32_t> flags) {
+    if (flags.ndim() != 1 || flags.shape(0) != code_object_ids.shape(0))
+      throw std::invalid_argument("length mismatch");
+    accumulate_impl(code_object_ids, offsets, exec_masks, &flags);
+  }
+
+  // Synchronize and read back (histogram, lane_histogram, overflow).
+  py::tuple read(bool also_reset) {
+    HIP_CHECK(hipSetDevice(device_));
+    py::array_t<uint32_t> hist(total_buckets_);
+    py::array_t<uint64_t> lanes(total_buckets_);
+    py::array_t<uint32_t> overflow(2);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    HIP_CHECK(hipMemcpy(hist.mutable_data(0), d_hist_,
+                        total_buckets_ * sizeof(uint32_t),
+                        hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(lanes.mutable_data(0), d_lane_hist_,
+                        total_buckets_ * sizeof(uint64_t),
+                        hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(overflow.mutable_data(0), d_overflow_,
+                        2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (also_reset) reset();
+    return py::make_tuple(hist, lanes, overflow);
+  }
+
+  // read() plus the stall matrix: (hist, lanes, overflow, stalls) with
+  // stalls shaped (total_buckets, 16), all zero if no flagged batch was
+  // ever accumulated.
+  py::tuple read_stalls(bool also_reset) {
+    HIP_CHECK(hipSetDevice(device_));
+    py::array_t<uint32_t> stalls(
+        {static_cast<py::ssize_t>(total_buckets_),
+         static_cast<py::ssize_t>(parca_gpu::kStallColumns)});
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    if (d_stall_ != nullptr)
+      HIP_CHECK(hipMemcpy(stalls.mutable_data(), d_stall_, stall_bytes(),
+                          hipMemcpyDeviceToHost));
+    else
+      memset(stalls.mutable_data(), 0, stall_bytes());
+    py::tuple base = read(also_reset);
+    return py::make_tuple(base[0], base[1], base[2], stalls);
+  }
+
+  uint64_t device_histogram_ptr() const {
+    return reinterpret_cast<uint64_t>(d_hist_);
+  }
+  uint32_t total_buckets() const { return total_buckets_; }
+
+ private:
+  size_t stall_bytes() const {
+    return static_cast<size_t>(total_buckets_) * parca_gpu::kStallColumns *
+           sizeof(uint32_t);
+  }
+
+  void accumulate_impl(py::array_t<uint64_t>& code_object_ids,
+                       py::array_t<uint64_t>& offsets,
+                       py::array_t<uint64_t>& exec_masks,
+                       py::array_t<uint32_t>* flags) {
     auto co = code_object_ids.unchecked<1>();
     auto off = offsets.unchecked<1>();
     uint32_t n = static_cast<uint32_t>(co.shape(0));
@@ -371,6 +462,22 @@ class DeviceBucketizer {
       HIP_CHECK(hipMalloc(&d_co_, cap_samples_ * sizeof(uint64_t)));
       HIP_CHECK(hipMalloc(&d_off_, cap_samples_ * sizeof(uint64_t)));
       HIP_CHECK(hipMalloc(&d_exec_, cap_samples_ * sizeof(uint64_t)));
+    }
+    if (flags != nullptr) {
+      if (d_stall_ == nullptr) {
+        HIP_CHECK(hipMalloc(&d_stall_, stall_bytes()));
+        HIP_CHECK(hipMemsetAsync(d_stall_, 0, stall_bytes(), stream_));
+      }
+      if (cap_flags_ < cap_samples_) {
+        if (d_flags_ != nullptr) HIP_CHECK(hipFree(d_flags_));
+        d_flags_ = nullptr;
+        cap_flags_ = 0;
+        HIP_CHECK(hipMalloc(&d_flags_, cap_samples_ * sizeof(uint32_t)));
+        cap_flags_ = cap_samples_;
+      }
+      HIP_CHECK(hipMemcpyAsync(d_flags_, flags->unchecked<1>().data(0),
+                               n * sizeof(uint32_t), hipMemcpyHostToDevice,
+                               stream_));
     }
     HIP_CHECK(hipMemcpyAsync(d_co_, co.data(0), n * sizeof(uint64_t),
                              hipMemcpyHostToDevice, stream_));
@@ -394,34 +501,11 @@ class DeviceBucketizer {
     args.histogram = d_hist_;
     args.lane_histogram = d_lane_hist_;
     args.overflow = d_overflow_;
+    args.sample_flags = flags != nullptr ? d_flags_ : nullptr;
+    args.stall_histogram = flags != nullptr ? d_stall_ : nullptr;
     parca_gpu::launch_bucketize(args, stream_);
   }
 
-  // Synchronize and read back (histogram, lane_histogram, overflow).
-  py::tuple read(bool also_reset) {
-    HIP_CHECK(hipSetDevice(device_));
-    py::array_t<uint32_t> hist(total_buckets_);
-    py::array_t<uint64_t> lanes(total_buckets_);
-    py::array_t<uint32_t> overflow(2);
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    HIP_CHECK(hipMemcpy(hist.mutable_data(0), d_hist_,
-                        total_buckets_ * sizeof(uint32_t),
-                        hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(lanes.mutable_data(0), d_lane_hist_,
-                        total_buckets_ * sizeof(uint64_t),
-                        hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(overflow.mutable_data(0), d_overflow_,
-                        2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (also_reset) reset();
-    return py::make_tuple(hist, lanes, overflow);
-  }
-
-  uint64_t device_histogram_ptr() const {
-    return reinterpret_cast<uint64_t>(d_hist_);
-  }
-  uint32_t total_buckets() const { return total_buckets_; }
-
- private:
   int device_;
   uint32_t bucket_shift_;
   uint32_t n_slots_ = 0;
@@ -436,6 +520,10 @@ class DeviceBucketizer {
   uint64_t* d_off_ = nullptr;
   uint64_t* d_exec_ = nullptr;
   uint32_t cap_samples_ = 0;
+  // Stall breakdown state, allocated by the first accumulate_flagged().
+  uint32_t* d_flags_ = nullptr;
+  uint32_t* d_stall_ = nullptr;
+  uint32_t cap_flags_ = 0;
 };
 
 // -- RCCL node merge ------------------------------------------------------
@@ -580,6 +668,14 @@ PYBIND11_MODULE(_gpu, m) {
 
   m.def("hip_device_count", &hip_device_count);
 
+  // The C++ packing of PCSample.flags, so a CPU test can pin the Python
+  // mirror (events.pack_pc_flags) to it.
+  m.def("pack_pc_flags", &pack_pc_flags, py::arg("stochastic"),
+        py::arg("valid"), py::arg("issued"), py::arg("inst_type"),
+        py::arg("reason"));
+  m.attr("N_STALL_COLUMNS") = static_cast<uint32_t>(kStallColumns);
+  m.def("split_pc_samples", &split_pc_samples, py::arg("samples"));
+
   // C-layout sizes so the Python struct decoders are layout-checked in
   // CPU tests (golden-bytes strategy).
   m.attr("SIZEOF_KERNEL_DISPATCH") =
@@ -620,7 +716,10 @@ PYBIND11_MODULE(_gpu, m) {
            py::arg("device"), py::arg("slot_ids"), py::arg("slot_offsets"),
            py::arg("bucket_shift"))
       .def("accumulate", &DeviceBucketizer::accumulate)
+      .def("accumulate_flagged", &DeviceBucketizer::accumulate_flagged)
       .def("read", &DeviceBucketizer::read, py::arg("also_reset") = true)
+      .def("read_stalls", &DeviceBucketizer::read_stalls,
+           py::arg("also_reset") = true)
       .def("reset", &DeviceBucketizer::reset)
       .def_property_readonly("total_buckets", &DeviceBucketizer::total_buckets)
       .def_property_readonly("device_histogram_ptr",

@@ -104,8 +104,42 @@ struct PCSample {
   uint64_t correlation_id;
   uint64_t hw_id;        // raw rocprofiler_pc_sampling_hw_id_v0_t bits
   uint32_t wave_in_group;
-  uint32_t flags;        // bit0: stochastic, bit1: valid-issue info
+  uint32_t flags;        // kPcFlag* bits below; 0 for host-trap samples
 };
+static_assert(sizeof(PCSample) == 64, "PCSample layout");
+
+// PCSample.flags layout. Host-trap records carry 0; every stochastic
+// record carries bit0|bit1 plus what the hardware reported about the
+// sampled wave's issue state.
+constexpr uint32_t kPcFlagStochastic = 1u << 0;
+constexpr uint32_t kPcFlagIssueValid = 1u << 1;  // bits 2..19 are meaningful
+constexpr uint32_t kPcFlagWaveIssued = 1u << 2;
+constexpr uint32_t kPcFlagInstTypeShift = 8;   // 5 bits, raw inst_type
+constexpr uint32_t kPcFlagInstTypeMask = 0x1F;
+constexpr uint32_t kPcFlagReasonShift = 16;    // 4 bits, raw reason_not_issued
+constexpr uint32_t kPcFlagReasonMask = 0xF;
+
+// Stall-reason histogram columns derived from the flags (mirrored by
+// gpu/events.py stall_column and by the bucketize kernel):
+//   bit1 clear        -> no column (the sample counts in the total only)
+//   bit2 set          -> kStallColumnIssued
+//   raw reason r <= 9 -> column r (the SDK's reason_not_issued enum)
+//   r in 10..15       -> kStallColumnUnknown
+// Columns 10..13 are reserved and never produced.
+constexpr uint32_t kStallColumns = 16;
+constexpr uint32_t kStallColumnUnknown = 14;
+constexpr uint32_t kStallColumnIssued = 15;
+
+// The one place the flags word is assembled; out-of-range inst_type and
+// reason values are truncated to their field widths.
+inline uint32_t pack_pc_flags(bool stochastic, bool valid, bool issued,
+                              uint32_t inst_type, uint32_t reason) {
+  return (stochastic ? kPcFlagStochastic : 0u) |
+         (valid ? kPcFlagIssueValid : 0u) |
+         (issued ? kPcFlagWaveIssued : 0u) |
+         ((inst_type & kPcFlagInstTypeMask) << kPcFlagInstTypeShift) |
+         ((reason & kPcFlagReasonMask) << kPcFlagReasonShift);
+}
 
 struct PCSampleBatchHeader {
   uint32_t gpu_index;

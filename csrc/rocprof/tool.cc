@@ -324,7 +324,9 @@ void pc_sampling_buffer_cb(rocprofiler_context_id_t /*ctx*/,
       s.correlation_id = r->correlation_id.internal;
       memcpy(&s.hw_id, &r->hw_id, sizeof(uint64_t));
       s.wave_in_group = r->wave_in_group;
-      s.flags = 1;
+      s.flags = pack_pc_flags(/*stochastic=*/true, /*valid=*/true,
+                              r->wave_issued != 0, r->inst_type,
+                              r->snapshot.reason_not_issued);
     } else {
       continue;  // invalid-sample records are dropped silently
     }

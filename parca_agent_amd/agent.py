@@ -244,6 +244,7 @@ class Agent:
                     shm_dir=f.rocm.shm_dir,
                     pc_flush_interval=f.profiling.duration,
                     bucket_shift=f.rocm.bucket_bits,
+                    stall_reasons=f.rocm.pc_stall_reasons,
                     processes=self.processes,
                     executables=self.executables,
                 )
@@ -284,6 +285,17 @@ class Agent:
             self.k8s_informer.stop()
         self.reporter.stop()
 
+    def tool_env(self, **overrides) -> dict:
+        """tool_env() for processes this agent is to profile, with the
+        --rocm-* flags applied (ring location and size, PC sampling and
+        its method); keyword arguments override them."""
+        r = self.flags.rocm
+        kwargs = dict(shm_dir=r.shm_dir, ring_bytes=self.flags.gpu_ring_bytes,
+                      pc_sampling=r.pc_sampling,
+                      pc_method=r.pc_sampling_method)
+        kwargs.update(overrides)
+        return tool_env(**kwargs)
+
     def stats(self) -> AgentStats:
         s = AgentStats()
         if self.cpu_service is not None:
@@ -319,7 +331,8 @@ def tool_env(shm_dir: str = "/dev/shm", defer_start: bool = False,
              ring_bytes: int = 32 << 20, pc_sampling: bool = True,
              pc_interval: Optional[int] = None,
              launch_stacks: bool = True,
-             heap_profiling: bool = False) -> dict:
+             heap_profiling: bool = False,
+             pc_method: str = "host_trap") -> dict:
     """Environment for a target HIP process to be profiled."""
     env = {
         "ROCP_TOOL_LIBRARIES": tool_library_path(),
@@ -334,6 +347,9 @@ def tool_env(shm_dir: str = "/dev/shm", defer_start: bool = False,
         env["PARCA_GPU_DEFER_START"] = "1"
     if pc_interval is not None:
         env["PARCA_GPU_PC_INTERVAL"] = str(pc_interval)
+    if pc_method != "host_trap":
+        # host_trap is the tool's own default: leave the variable unset.
+        env["PARCA_GPU_PC_METHOD"] = pc_method
     if heap_profiling:
         # Allocation sampler for OOM heap profiles (oom/heap.py); its
         # shm state outlives the process so the agent can ship profiles

@@ -144,6 +144,9 @@ class RocmFlags:
     pc_sampling: bool = True
     pc_sampling_interval: int = 1048576  # cycles between PC samples
     pc_sampling_method: str = "host_trap"  # host_trap | stochastic
+    # Split gpu_pcsample by stall reason where samples carry issue info
+    # (stochastic sampling); host-trap samples are unaffected.
+    pc_stall_reasons: bool = True
     kernel_batch_size: int = 100  # parcagpu.go:96 batch of kernel timings
     # log2 of the PC-bucket size in bytes for the HIP histogram:
     # 6 => 64-byte buckets (≈ a few instructions).
@@ -311,6 +314,8 @@ _HELP = {
     "rocm-enable": "GPU subsystem (rocprofiler tool rings, kernel "
                    "timings, PC sampling).",
     "rocm-pc-sampling": "gfx950 PC sampling where the driver exposes it.",
+    "rocm-pc-stall-reasons": "Label gpu_pcsample with stall_reason "
+                             "(stochastic PC sampling only).",
     "rocm-ring-scale-factor": "Per-process GPU ring = 32 MiB << n.",
     "rocm-merge-node-profiles": "Daemon-side merged node-level GPU "
                                 "pprof across all local GPUs.",

@@ -45,6 +45,73 @@ PC_SAMPLE_DTYPE = np.dtype([
 ])
 
 
+# -- PCSample.flags (ring.h kPcFlag*, pack_pc_flags) -----------------------
+#
+#   bit 0       stochastic record
+#   bit 1       issue info valid (every stochastic record, no host-trap one)
+#   bit 2       wave_issued
+#   bits 8-12   inst_type (raw)
+#   bits 16-19  snapshot.reason_not_issued (raw)
+
+PC_FLAG_STOCHASTIC = 1 << 0
+PC_FLAG_ISSUE_VALID = 1 << 1
+PC_FLAG_WAVE_ISSUED = 1 << 2
+PC_FLAG_INST_TYPE_SHIFT = 8
+PC_FLAG_INST_TYPE_MASK = 0x1F
+PC_FLAG_REASON_SHIFT = 16
+PC_FLAG_REASON_MASK = 0xF
+
+# Stall-reason histogram columns: 0..9 are the SDK's reason_not_issued
+# enum, 10..13 are never produced, 14 collects raw reasons the enum does
+# not define, 15 is "the wave issued an instruction".
+N_STALL_COLUMNS = 16
+STALL_COLUMN_UNKNOWN = 14
+STALL_COLUMN_ISSUED = 15
+NO_STALL_COLUMN = -1  # stall_column() of a sample without issue info
+STALL_COLUMN_NAMES = (
+    "none",
+    "no_instruction_available",
+    "alu_dependency",
+    "waitcnt",
+    "internal_instruction",
+    "barrier_wait",
+    "arbiter_not_win",
+    "arbiter_win_ex_stall",
+    "other_wait",
+    "sleep_wait",
+    "reserved_10",
+    "reserved_11",
+    "reserved_12",
+    "reserved_13",
+    "unknown",
+    "issued",
+)
+
+
+def pack_pc_flags(stochastic, valid, issued, inst_type: int,
+                  reason: int) -> int:
+    """Python mirror of ring.h pack_pc_flags (pinned to it in
+    tests/test_pc_stall_reasons.py)."""
+    return ((PC_FLAG_STOCHASTIC if stochastic else 0)
+            | (PC_FLAG_ISSUE_VALID if valid else 0)
+            | (PC_FLAG_WAVE_ISSUED if issued else 0)
+            | ((int(inst_type) & PC_FLAG_INST_TYPE_MASK)
+               << PC_FLAG_INST_TYPE_SHIFT)
+            | ((int(reason) & PC_FLAG_REASON_MASK) << PC_FLAG_REASON_SHIFT))
+
+
+def stall_column(flags):
+    """Stall column of each flags word (vectorised; a scalar gives a
+    0-d array): NO_STALL_COLUMN where bit 1 is clear, STALL_COLUMN_ISSUED
+    where bit 2 is set, else the raw reason, with reasons above 9 folded
+    into STALL_COLUMN_UNKNOWN."""
+    f = np.asarray(flags).astype(np.int64)
+    reason = (f >> PC_FLAG_REASON_SHIFT) & PC_FLAG_REASON_MASK
+    col = np.where(reason <= 9, reason, STALL_COLUMN_UNKNOWN)
+    col = np.where(f & PC_FLAG_WAVE_ISSUED, STALL_COLUMN_ISSUED, col)
+    return np.where(f & PC_FLAG_ISSUE_VALID, col, NO_STALL_COLUMN)
+
+
 @dataclass
 class KernelDispatch:
     correlation_id: int

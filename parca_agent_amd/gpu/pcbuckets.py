@@ -9,6 +9,10 @@ Two backends with identical semantics:
   hosts (and for CPU tests — both backends are verified against each
   other in tests/test_gpu_bucketize.py).
 
+Both also keep, per bucket, a 16-column stall-reason row fed by the
+samples whose flags carry issue info (read_with_stalls; column table in
+events.py), with stalls[b].sum() <= hist[b].
+
 Bucket space: each (pid, code_object_id) gets a contiguous slot of
 ceil(load_size / 2^bucket_shift) buckets. The layout is rebuilt when new
 code objects appear (rare) — pending device state is flushed first.
@@ -21,6 +25,13 @@ from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
+
+from .events import (
+    N_STALL_COLUMNS,
+    NO_STALL_COLUMN,
+    PC_FLAG_ISSUE_VALID,
+    stall_column,
+)
 
 log = logging.getLogger("parca_agent_amd.gpu.pcbuckets")
 
@@ -113,6 +124,8 @@ class HostAccumulator:
     def __init__(self, layout: BucketLayout) -> None:
         self.layout = layout
         self._hists: Dict[int, Tuple[np.ndarray, np.ndarray]] = {}
+        # gpu -> (total_buckets, N_STALL_COLUMNS) stall-reason counts
+        self._stalls: Dict[int, np.ndarray] = {}
         self.unknown_code_object = 0
         self.out_of_range = 0
 
@@ -128,6 +141,11 @@ class HostAccumulator:
             pair = (hist, lanes)
             self._hists[gpu] = pair
         return pair
+
+    def _stall_array(self, gpu: int) -> np.ndarray:
+        self._stalls[gpu] = _grown_stalls(self._stalls.get(gpu),
+                                          self.layout.total_buckets)
+        return self._stalls[gpu]
 
     def accumulate(self, pid: int, samples: np.ndarray,
                    gpu: int = -1) -> None:
@@ -163,6 +181,11 @@ class HostAccumulator:
         np.add.at(hist, buckets, 1)
         lanes = _popcount64(exec_masks[known][in_range])
         np.add.at(lane_hist, buckets, lanes)
+        cols = stall_column(samples["flags"][known][in_range])
+        has_col = cols != NO_STALL_COLUMN
+        if has_col.any():
+            np.add.at(self._stall_array(gpu),
+                      (buckets[has_col].astype(np.intp), cols[has_col]), 1)
 
     def read(self, also_reset: bool = True
              ) -> Dict[int, Tuple[np.ndarray, np.ndarray]]:
@@ -174,7 +197,36 @@ class HostAccumulator:
             if also_reset:
                 h[:] = 0
                 l[:] = 0
+                if gpu in self._stalls:
+                    self._stalls[gpu][:] = 0
         return out
+
+    def read_with_stalls(self, also_reset: bool = True
+                         ) -> Dict[int, Tuple[np.ndarray, np.ndarray,
+                                              np.ndarray]]:
+        """gpu -> (hist, lane_hist, stalls); stalls is (total_buckets,
+        N_STALL_COLUMNS) uint64 with stalls[b].sum() <= hist[b]."""
+        out = {}
+        for gpu in list(self._hists):
+            h, l = self._arrays(gpu)
+            s = self._stall_array(gpu)
+            out[gpu] = (h.copy(), l.copy(), s.copy())
+            if also_reset:
+                h[:] = 0
+                l[:] = 0
+                s[:] = 0
+        return out
+
+
+def _grown_stalls(arr: Optional[np.ndarray], total: int) -> np.ndarray:
+    """The stall matrix sized for the current layout, old rows kept (the
+    layout is append-only, so rows never move)."""
+    if arr is not None and len(arr) >= total:
+        return arr
+    out = np.zeros((total, N_STALL_COLUMNS), dtype=np.uint64)
+    if arr is not None:
+        out[: len(arr)] = arr
+    return out
 
 
 def _popcount64(arr: np.ndarray) -> np.ndarray:
@@ -219,6 +271,12 @@ class DeviceAccumulator:
         # per gpu. Global slot offsets are STABLE (the layout is
         # append-only), so folding early is safe.
         self._pending: Dict[int, Tuple[np.ndarray, np.ndarray]] = {}
+        # Same carryover for the stall matrices; a gpu appears here only
+        # once stall counts exist for it.
+        self._pending_stalls: Dict[int, np.ndarray] = {}
+        # Bucketizers that were handed a flagged batch: only those hold a
+        # device stall matrix worth reading back.
+        self._flagged: set = set()
 
     def layout_changed(self) -> None:
         self._gen += 1
@@ -236,11 +294,18 @@ class DeviceAccumulator:
             self._pending[gpu] = pair
         return pair
 
+    def _pending_stall_array(self, gpu: int) -> np.ndarray:
+        self._pending_stalls[gpu] = _grown_stalls(
+            self._pending_stalls.get(gpu), self.layout.total_buckets)
+        return self._pending_stalls[gpu]
+
     def _fold_global(self, pid: int, gpu: int, h: np.ndarray,
-                     l: np.ndarray) -> None:
-        """Fold one pid's LOCAL-space histograms into the pending global
-        arrays using that pid's current base/offset tables."""
+                     l: np.ndarray, s: Optional[np.ndarray] = None) -> None:
+        """Fold one pid's LOCAL-space histograms (and stall rows, when
+        given) into the pending global arrays using that pid's current
+        base/offset tables."""
         hist, lanes = self._pending_arrays(gpu)
+        stalls = self._pending_stall_array(gpu) if s is not None else None
         base = self._bases[pid]
         offs = self._local_offsets[pid]
         for i in range(len(base)):
@@ -248,6 +313,23 @@ class DeviceAccumulator:
             g = int(base[i])
             hist[g : g + (hi - lo)] += h[lo:hi]
             lanes[g : g + (hi - lo)] += l[lo:hi]
+            if stalls is not None:
+                stalls[g : g + (hi - lo)] += s[lo:hi]
+
+    def _drain(self, pid: int, gpu: int, b, with_stalls: bool) -> None:
+        """Read-and-reset one bucketizer into the pending global arrays.
+        Without with_stalls its stall counts are discarded (the native
+        read clears them)."""
+        s = None
+        if with_stalls and (pid, gpu) in self._flagged:
+            h, l, overflow, s = b.read_stalls(True)
+            s = s.astype(np.uint64)
+        else:
+            h, l, overflow = b.read(True)
+        self.unknown_code_object += int(overflow[0])
+        self.out_of_range += int(overflow[1])
+        self._fold_global(pid, gpu, h.astype(np.uint64),
+                          l.astype(np.uint64), s)
 
     def _bucketizer(self, pid: int, gpu: int):
         key = (pid, gpu)
@@ -256,11 +338,8 @@ class DeviceAccumulator:
             # (with the OLD tables) before rebuilding for the new layout.
             old = self._buckets.pop(key, None)
             if old is not None:
-                hist, lanes, overflow = old.read(True)
-                self.unknown_code_object += int(overflow[0])
-                self.out_of_range += int(overflow[1])
-                self._fold_global(pid, gpu, hist.astype(np.uint64),
-                                  lanes.astype(np.uint64))
+                self._drain(pid, gpu, old, with_stalls=True)
+                self._flagged.discard(key)
             slot_ids, local_offsets, global_base = \
                 self.layout.device_tables(pid)
             if len(slot_ids) == 0:
@@ -279,23 +358,30 @@ class DeviceAccumulator:
         if b is None:
             self.unknown_code_object += len(samples)
             return
-        b.accumulate(np.ascontiguousarray(samples["code_object_id"]),
-                     np.ascontiguousarray(samples["code_object_offset"]),
-                     np.ascontiguousarray(samples["exec_mask"]))
+        # One native pass over the 64-byte records yields all four columns
+        # and the OR of the flags, so deciding the entry point costs no
+        # extra sweep over the batch.
+        co, off, exec_masks, flags, flags_or = \
+            self._native.split_pc_samples(samples)
+        # Host-trap batches (no sample with issue info) keep the plain
+        # entry point: no flags upload, no stall matrix, same kernels.
+        if flags_or & PC_FLAG_ISSUE_VALID:
+            self._flagged.add((pid, gpu))
+            b.accumulate_flagged(co, off, exec_masks, flags)
+        else:
+            b.accumulate(co, off, exec_masks)
 
     def read(self, also_reset: bool = True
              ) -> Dict[int, Tuple[np.ndarray, np.ndarray]]:
         """Fold all per-(pid, gpu) device histograms plus carryover into
         per-GPU arrays over the global bucket space and reset. Always
         destructive (the device state is drained into the result); the
-        parameter exists for API parity with HostAccumulator."""
+        parameter exists for API parity with HostAccumulator. Stall
+        counts gathered so far are dropped with it."""
         del also_reset
         for (pid, gpu), b in list(self._buckets.items()):
-            h, l, overflow = b.read(True)
-            self.unknown_code_object += int(overflow[0])
-            self.out_of_range += int(overflow[1])
-            self._fold_global(pid, gpu, h.astype(np.uint64),
-                              l.astype(np.uint64))
+            self._drain(pid, gpu, b, with_stalls=False)
+        self._pending_stalls.clear()
         out = {}
         for gpu in list(self._pending):
             hist, lanes = self._pending_arrays(gpu)
@@ -304,6 +390,25 @@ class DeviceAccumulator:
             lanes[:] = 0
         return out
 
+    def read_with_stalls(self, also_reset: bool = True
+                         ) -> Dict[int, Tuple[np.ndarray, np.ndarray,
+                                              np.ndarray]]:
+        """read() plus, per gpu, the (total_buckets, N_STALL_COLUMNS)
+        uint64 stall matrix. Destructive like read()."""
+        del also_reset
+        for (pid, gpu), b in list(self._buckets.items()):
+            self._drain(pid, gpu, b, with_stalls=True)
+        out = {}
+        for gpu in list(self._pending):
+            hist, lanes = self._pending_arrays(gpu)
+            stalls = self._pending_stalls.pop(gpu, None)
+            stalls = _grown_stalls(stalls, self.layout.total_buckets)
+            out[gpu] = (hist.copy(), lanes.copy(), stalls)
+            hist[:] = 0
+            lanes[:] = 0
+        return out
+
     def drop_process(self, pid: int) -> None:
         for key in [k for k in self._buckets if k[0] == pid]:
             self._buckets.pop(key, None)
+            self._flagged.discard(key)

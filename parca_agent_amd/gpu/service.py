@@ -88,6 +88,7 @@ class GPUProfilerService:
         on_executable=None,
         on_code_object=None,
         clock_offset_ns: Optional[int] = None,
+        stall_reasons: bool = True,
     ) -> None:
         from ..native import gpu as native_gpu
 
@@ -96,6 +97,9 @@ class GPUProfilerService:
         self.shm_dir = shm_dir
         self.poll_interval = poll_interval
         self.pc_flush_interval = pc_flush_interval
+        # Split gpu_pcsample traces by stall reason where the samples
+        # carry issue info (stochastic sampling); off = one trace per PC.
+        self.stall_reasons = stall_reasons
         self.metrics = GpuServiceMetrics()
 
         self.processes = processes or ProcessTable()
@@ -286,10 +290,13 @@ class GPUProfilerService:
                     dev = DeviceAccumulator(self.layout)
                     # fold anything the host accumulator gathered in the
                     # race window into the device pending arrays
-                    for g, (h, l) in self.accumulator.read(True).items():
+                    for g, (h, l, st) in \
+                            self.accumulator.read_with_stalls(True).items():
                         dp = dev._pending_arrays(g)
                         dp[0][: len(h)] += h
                         dp[1][: len(l)] += l
+                        if st.any() and hasattr(dev, "_pending_stall_array"):
+                            dev._pending_stall_array(g)[: len(st)] += st
                     self.accumulator = dev
                     log.info("device bucketize initialized (first PC "
                              "samples arrived)")
@@ -437,12 +444,19 @@ class GPUProfilerService:
         stream per source GPU (per-GPU fan-out for the daemon shape)."""
         if self.layout.total_buckets == 0:
             return
+        if self.stall_reasons and hasattr(self.accumulator,
+                                          "read_with_stalls"):
+            for gpu, (hist, lane_hist, stalls) in sorted(
+                    self.accumulator.read_with_stalls(True).items()):
+                self._flush_pc_gpu(gpu, hist, lane_hist, stalls)
+            return
         for gpu, (hist, lane_hist) in sorted(
                 self.accumulator.read(True).items()):
             self._flush_pc_gpu(gpu, hist, lane_hist)
 
     def _flush_pc_gpu(self, gpu: int, hist: np.ndarray,
-                      lane_hist: np.ndarray) -> None:
+                      lane_hist: np.ndarray,
+                      stalls: Optional[np.ndarray] = None) -> None:
         nonzero = np.nonzero(hist)[0]
         if len(nonzero) == 0:
             return
@@ -466,13 +480,6 @@ class GPUProfilerService:
                 func = ""
             frames = (Frame(kind=FrameType.GPU_PC, address=address,
                             mapping=mapping, function_name=func),)
-            meta = TraceEventMeta(
-                timestamp_ns=now_ns,
-                pid=pid,
-                origin=TraceOrigin.GPU_PC,
-                value=int(hist[bucket]),
-                gpu_id=gpu,
-            )
             # Wave-occupancy view: mean active lanes (of 64) at this PC,
             # from the exec-mask popcounts the bucketize kernel sums —
             # divergence shows up as avg_active_lanes << 64.
@@ -481,9 +488,30 @@ class GPUProfilerService:
                 avg_lanes = int(round(
                     int(lane_hist[bucket]) / int(hist[bucket])))
                 labels = (("avg_active_lanes", str(avg_lanes)),)
-            self.reporter.report_trace_event(
-                Trace(frames=frames, custom_labels=labels), meta)
-            self.metrics.pc_buckets_reported += 1
+            # Stall breakdown: one trace per non-zero stall column, plus
+            # an unlabelled one for the samples that carried no issue
+            # info; a bucket with an all-zero row stays one trace.
+            total = int(hist[bucket])
+            parts = []
+            if stalls is not None:
+                row = stalls[bucket]
+                for col in np.nonzero(row)[0]:
+                    parts.append((int(row[col]), labels + ((
+                        "stall_reason", ev.STALL_COLUMN_NAMES[col]),)))
+                    total -= int(row[col])
+            if total > 0:
+                parts.append((total, labels))
+            for value, part_labels in parts:
+                meta = TraceEventMeta(
+                    timestamp_ns=now_ns,
+                    pid=pid,
+                    origin=TraceOrigin.GPU_PC,
+                    value=value,
+                    gpu_id=gpu,
+                )
+                self.reporter.report_trace_event(
+                    Trace(frames=frames, custom_labels=part_labels), meta)
+                self.metrics.pc_buckets_reported += 1
 
 
 def demangle_kernel(name: str) -> str:

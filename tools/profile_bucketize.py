@@ -1,21 +1,39 @@
 #!/usr/bin/env python3
 """rocprofv3 target: run the CDNA4 bucketize kernel in a tight loop so
-per-kernel stats/counters can be collected (profiles/ evidence)."""
+per-kernel stats/counters can be collected (profiles/ evidence).
 
+Usage: profile_bucketize.py [n] [iters] [--stalls] [--reps R]
+
+--stalls gives the same synthetic stream PCSample.flags with issue info
+(about 30 % of samples keep flags 0), so the stall-reason launch paths run
+instead of the flag-less ones. Each of the R repetitions times `iters`
+accumulates of both streams plus the read-back and prints its rate."""
+
+import argparse
 import os
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import numpy as np
 
+from parca_agent_amd.gpu import events as ev
 from parca_agent_amd.gpu.events import PC_SAMPLE_DTYPE
 from parca_agent_amd.gpu.pcbuckets import BucketLayout, DeviceAccumulator
 
 
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 4_000_000
-    iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+    ap = argparse.ArgumentParser()
+    ap.add_argument("n", nargs="?", type=int, default=4_000_000)
+    ap.add_argument("iters", nargs="?", type=int, default=20)
+    ap.add_argument("--stalls", action="store_true",
+                    help="flag the samples: stall-reason kernels")
+    ap.add_argument("--reps", type=int, default=1,
+                    help="timed repetitions after one warm-up")
+    args = ap.parse_args()
+    n, iters = args.n, args.iters
+
     rng = np.random.default_rng(1)
     layout = BucketLayout(bucket_shift=6)
     layout.add(pid=1, code_object_id=1, load_size=1 << 20)  # 16K buckets: LDS path
@@ -27,11 +45,39 @@ def main():
     samples["exec_mask"] = rng.integers(1, 1 << 63, size=n, dtype=np.uint64)
     big = samples.copy()
     big["code_object_offset"] = rng.integers(0, 64 * 40000, size=n)
-    for _ in range(iters):
-        dev.accumulate(1, samples)   # LDS-staged variant
-        dev.accumulate(2, big)       # global-atomics variant
-    hist, _ = dev.read()[-1]
-    print("total bucketed:", int(hist.sum()))
+    # Drawn whether used or not, so both modes see the same stream.
+    flags = (rng.integers(0, 16, size=n).astype(np.uint32)
+             << ev.PC_FLAG_REASON_SHIFT) | np.uint32(
+                 ev.PC_FLAG_STOCHASTIC | ev.PC_FLAG_ISSUE_VALID)
+    flags[rng.random(n) < 0.2] |= np.uint32(ev.PC_FLAG_WAVE_ISSUED)
+    flags[rng.random(n) < 0.3] = 0
+    if args.stalls:
+        samples["flags"] = flags
+        big["flags"] = flags
+
+    def one_rep():
+        for _ in range(iters):
+            dev.accumulate(1, samples)   # LDS-staged variant
+            dev.accumulate(2, big)       # global-atomics variant
+        if args.stalls:
+            hist, _, stalls = dev.read_with_stalls()[-1]
+            return int(hist.sum()), int(stalls.sum())
+        hist, _ = dev.read()[-1]
+        return int(hist.sum()), 0
+
+    one_rep()  # warm-up: allocations, code-object load
+    rates = []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        total, stalled = one_rep()
+        dt = time.perf_counter() - t0
+        rates.append(2 * iters * n / dt / 1e6)
+        print(f"rep: {rates[-1]:.1f} M samples/s")
+    print("total bucketed:", total, "with stall column:", stalled)
+    print(f"mode={'stalls' if args.stalls else 'plain'} n={n} iters={iters} "
+          f"rates_M_per_s={[round(r, 1) for r in rates]} "
+          f"median={np.median(rates):.1f} min={min(rates):.1f} "
+          f"max={max(rates):.1f}")
 
 
 if __name__ == "__main__":

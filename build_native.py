@@ -7,6 +7,7 @@ gpurun-ignored). Components:
 
   _sampler.so          g++      perf_event_open CPU sampler (pybind11)
   _gpu.so              hipcc    shm-ring reader + CDNA4 PC-bucketing kernel +
+                                sparse-readback compaction kernel +
                                 RCCL node merge (pybind11, gfx950)
   libparca_rocprof.so  g++      rocprofiler-sdk interception tool, loaded into
                                 target HIP processes via ROCP_TOOL_LIBRARIES
@@ -94,12 +95,14 @@ def build_rocprof_tool(debug: bool = False, force: bool = False) -> Path:
 
 
 def build_gpu(debug: bool = False, force: bool = False) -> Path:
-    srcs = [CSRC / "gpu" / "gpu_module.cc", CSRC / "gpu" / "bucketize.hip"]
+    srcs = [CSRC / "gpu" / "gpu_module.cc", CSRC / "gpu" / "bucketize.hip",
+            CSRC / "gpu" / "compact.hip"]
     srcs = [s for s in srcs if s.exists()]
     out = OUT / f"_gpu{EXT_SUFFIX}"
     if not srcs:
         return out
-    deps = srcs + [CSRC / "gpu" / "bucketize.h", CSRC / "rocprof" / "ring.h"]
+    deps = srcs + [CSRC / "gpu" / "bucketize.h", CSRC / "gpu" / "compact.h",
+                   CSRC / "rocprof" / "ring.h"]
     if not force and not _needs_build(out, deps):
         return out
     opt = "-O1" if debug else "-O3"

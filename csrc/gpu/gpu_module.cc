@@ -1,5 +1,6 @@
 // Agent-side GPU extension (_gpu): shm ring consumer, device PC-sample
-// bucketing (bucketize.hip), RCCL node-merge over xGMI.
+// bucketing (bucketize.hip) with sparse readback (compact.hip), RCCL
+// node-merge over xGMI.
 //
 // The consumer half of the parcagpu analog (reference:
 // parcagpu/parcagpu.go:69-213); the RCCL merge has no reference analog
@@ -9,8 +10,10 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <numeric>
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
@@ -26,6 +29,7 @@
 #include <rccl/rccl.h>
 
 #include "gpu/bucketize.h"
+#include "gpu/compact.h"
 #include "rocprof/ring.h"
 
 namespace py = pybind11;
@@ -355,7 +359,12 @@ class DeviceBucketizer {
                     static_cast<void*>(d_overflow_), static_cast<void*>(d_co_),
                     static_cast<void*>(d_off_), static_cast<void*>(d_exec_),
                     static_cast<void*>(d_flags_),
-                    static_cast<void*>(d_stall_)})
+                    static_cast<void*>(d_stall_),
+                    static_cast<void*>(d_out_bucket_),
+                    static_cast<void*>(d_out_count_),
+                    static_cast<void*>(d_out_lanes_),
+                    static_cast<void*>(d_out_stall_),
+                    static_cast<void*>(d_out_n_)})
       if (p) (void)hipFree(p);
     if (stream_) (void)hipStreamDestroy(stream_);
   }
@@ -370,6 +379,7 @@ class DeviceBucketizer {
     if (d_stall_ != nullptr)
       HIP_CHECK(hipMemsetAsync(d_stall_, 0, stall_bytes(), stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
+    samples_ = 0;
   }
 
   // Accumulate one batch of samples (SoA u64 arrays) into the device
@@ -431,6 +441,77 @@ class DeviceBucketizer {
     return py::make_tuple(base[0], base[1], base[2], stalls);
   }
 
+  // The touched buckets only: (buckets, counts, lanes, stalls, overflow)
+  // with k = number of buckets whose count is non-zero, sorted ascending
+  // by bucket, stalls shaped (k, 16) and all zero if no flagged batch was
+  // ever accumulated. The compaction runs on the device (compact.hip), so
+  // the copy back and the host work are O(k), not O(total_buckets). With
+  // also_reset the kernel zeroes what it emits in place — afterwards the
+  // dense arrays are all zero without a memset over them.
+  py::tuple read_sparse(bool also_reset) {
+    HIP_CHECK(hipSetDevice(device_));
+    py::array_t<uint32_t> overflow(2);
+    uint32_t* ovf = overflow.mutable_data(0);
+    ovf[0] = ovf[1] = 0;
+    // Every sample adds 1 to at most one bucket, so the samples since the
+    // last reset bound the non-zero buckets exactly; none means nothing
+    // was launched either, and the overflow words are still zero.
+    if (samples_ == 0) return sparse_result(0, overflow, nullptr);
+
+    uint32_t capacity = static_cast<uint32_t>(
+        std::min<uint64_t>(total_buckets_, samples_));
+    ensure_sparse(capacity, d_stall_ != nullptr);
+    parca_gpu::CompactArgs args{};
+    args.histogram = d_hist_;
+    args.lane_histogram = d_lane_hist_;
+    args.stall_histogram = d_stall_;
+    args.total_buckets = total_buckets_;
+    args.capacity = capacity;
+    args.clear = also_reset ? 1u : 0u;
+    args.out_bucket = d_out_bucket_;
+    args.out_count = d_out_count_;
+    args.out_lanes = d_out_lanes_;
+    args.out_stall = d_stall_ != nullptr ? d_out_stall_ : nullptr;
+    args.out_n = d_out_n_;
+    parca_gpu::launch_compact(args, stream_);  // zeroes out_n first
+    uint32_t k = 0;
+    HIP_CHECK(hipMemcpyAsync(&k, d_out_n_, sizeof(k), hipMemcpyDeviceToHost,
+                             stream_));
+    HIP_CHECK(hipMemcpyAsync(ovf, d_overflow_, 2 * sizeof(uint32_t),
+                             hipMemcpyDeviceToHost, stream_));
+    if (also_reset)
+      HIP_CHECK(hipMemsetAsync(d_overflow_, 0, 2 * sizeof(uint32_t), stream_));
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipStreamSynchronize(stream_));
+    }
+    if (k > capacity)
+      throw std::runtime_error("read_sparse: " + std::to_string(k) +
+                               " touched buckets exceed the capacity of " +
+                               std::to_string(capacity));
+    if (also_reset) samples_ = 0;
+
+    SparseHost host;
+    host.bucket.resize(k);
+    host.count.resize(k);
+    host.lanes.resize(k);
+    if (k != 0) {
+      HIP_CHECK(hipMemcpy(host.bucket.data(), d_out_bucket_,
+                          k * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(host.count.data(), d_out_count_,
+                          k * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(host.lanes.data(), d_out_lanes_,
+                          k * sizeof(uint64_t), hipMemcpyDeviceToHost));
+      if (d_stall_ != nullptr) {
+        host.stall.resize(static_cast<size_t>(k) * parca_gpu::kStallColumns);
+        HIP_CHECK(hipMemcpy(host.stall.data(), d_out_stall_,
+                            host.stall.size() * sizeof(uint32_t),
+                            hipMemcpyDeviceToHost));
+      }
+    }
+    return sparse_result(k, overflow, &host);
+  }
+
   uint64_t device_histogram_ptr() const {
     return reinterpret_cast<uint64_t>(d_hist_);
   }
@@ -440,6 +521,77 @@ class DeviceBucketizer {
   size_t stall_bytes() const {
     return static_cast<size_t>(total_buckets_) * parca_gpu::kStallColumns *
            sizeof(uint32_t);
+  }
+
+  // Entries as the kernel left them: ordered inside a reservation only.
+  struct SparseHost {
+    std::vector<uint32_t> bucket, count, stall;
+    std::vector<uint64_t> lanes;
+  };
+
+  // Grow-only output buffers of the compaction, sized to the capacity the
+  // sample counter allows; the stall rows only once a stall matrix exists.
+  void ensure_sparse(uint32_t capacity, bool with_stall) {
+    if (d_out_n_ == nullptr) HIP_CHECK(hipMalloc(&d_out_n_, sizeof(uint32_t)));
+    if (capacity > cap_out_) {
+      for (void* p : {static_cast<void*>(d_out_bucket_),
+                      static_cast<void*>(d_out_count_),
+                      static_cast<void*>(d_out_lanes_)})
+        if (p) HIP_CHECK(hipFree(p));
+      d_out_bucket_ = d_out_count_ = nullptr;
+      d_out_lanes_ = nullptr;
+      cap_out_ = 0;
+      HIP_CHECK(hipMalloc(&d_out_bucket_, capacity * sizeof(uint32_t)));
+      HIP_CHECK(hipMalloc(&d_out_count_, capacity * sizeof(uint32_t)));
+      HIP_CHECK(hipMalloc(&d_out_lanes_, capacity * sizeof(uint64_t)));
+      cap_out_ = capacity;
+    }
+    if (with_stall && capacity > cap_out_stall_) {
+      if (d_out_stall_) HIP_CHECK(hipFree(d_out_stall_));
+      d_out_stall_ = nullptr;
+      cap_out_stall_ = 0;
+      HIP_CHECK(hipMalloc(&d_out_stall_, static_cast<size_t>(capacity) *
+                                             parca_gpu::kStallColumns *
+                                             sizeof(uint32_t)));
+      cap_out_stall_ = capacity;
+    }
+  }
+
+  // Sort the k entries ascending by bucket (GIL released) into the numpy
+  // arrays read_sparse returns. Buckets are unique: one entry per bucket.
+  static py::tuple sparse_result(uint32_t k, py::array_t<uint32_t> overflow,
+                                 const SparseHost* host) {
+    constexpr uint32_t kCols = parca_gpu::kStallColumns;
+    py::array_t<uint32_t> buckets(k), counts(k);
+    py::array_t<uint64_t> lanes(k);
+    py::array_t<uint32_t> stalls({static_cast<py::ssize_t>(k),
+                                  static_cast<py::ssize_t>(kCols)});
+    if (k != 0) {
+      uint32_t* b = buckets.mutable_data(0);
+      uint32_t* c = counts.mutable_data(0);
+      uint64_t* l = lanes.mutable_data(0);
+      uint32_t* s = stalls.mutable_data();
+      py::gil_scoped_release rel;
+      std::vector<uint32_t> order(k);
+      std::iota(order.begin(), order.end(), 0u);
+      std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        return host->bucket[x] < host->bucket[y];
+      });
+      for (uint32_t i = 0; i < k; ++i) {
+        uint32_t from = order[i];
+        b[i] = host->bucket[from];
+        c[i] = host->count[from];
+        l[i] = host->lanes[from];
+        if (!host->stall.empty())
+          memcpy(s + static_cast<size_t>(i) * kCols,
+                 host->stall.data() + static_cast<size_t>(from) * kCols,
+                 kCols * sizeof(uint32_t));
+        else
+          memset(s + static_cast<size_t>(i) * kCols, 0,
+                 kCols * sizeof(uint32_t));
+      }
+    }
+    return py::make_tuple(buckets, counts, lanes, stalls, overflow);
   }
 
   void accumulate_impl(py::array_t<uint64_t>& code_object_ids,
@@ -504,6 +656,7 @@ class DeviceBucketizer {
     args.sample_flags = flags != nullptr ? d_flags_ : nullptr;
     args.stall_histogram = flags != nullptr ? d_stall_ : nullptr;
     parca_gpu::launch_bucketize(args, stream_);
+    samples_ += n;
   }
 
   int device_;
@@ -524,6 +677,16 @@ class DeviceBucketizer {
   uint32_t* d_flags_ = nullptr;
   uint32_t* d_stall_ = nullptr;
   uint32_t cap_flags_ = 0;
+  // Sparse readback state (read_sparse): samples accumulated since the
+  // last reset, and the compaction's grow-only output buffers.
+  uint64_t samples_ = 0;
+  uint32_t* d_out_bucket_ = nullptr;
+  uint32_t* d_out_count_ = nullptr;
+  uint64_t* d_out_lanes_ = nullptr;
+  uint32_t* d_out_stall_ = nullptr;
+  uint32_t* d_out_n_ = nullptr;
+  uint32_t cap_out_ = 0;
+  uint32_t cap_out_stall_ = 0;
 };
 
 // -- RCCL node merge ------------------------------------------------------
@@ -719,6 +882,8 @@ PYBIND11_MODULE(_gpu, m) {
       .def("accumulate_flagged", &DeviceBucketizer::accumulate_flagged)
       .def("read", &DeviceBucketizer::read, py::arg("also_reset") = true)
       .def("read_stalls", &DeviceBucketizer::read_stalls,
+           py::arg("also_reset") = true)
+      .def("read_sparse", &DeviceBucketizer::read_sparse,
            py::arg("also_reset") = true)
       .def("reset", &DeviceBucketizer::reset)
       .def_property_readonly("total_buckets", &DeviceBucketizer::total_buckets)

@@ -13,6 +13,18 @@ Both also keep, per bucket, a 16-column stall-reason row fed by the
 samples whose flags carry issue info (read_with_stalls; column table in
 events.py), with stalls[b].sum() <= hist[b].
 
+Sparse read (both backends): read_sparse(also_reset=True) returns, per
+gpu, (buckets, hist, lanes, stalls) for the touched buckets only —
+buckets int64[k], ascending, unique, in the global bucket space; hist and
+lanes uint64[k]; stalls uint64[k, N_STALL_COLUMNS]. For every gpu it
+equals np.nonzero of the hist read_with_stalls would have returned for
+the same state, and the rows at those indices; a gpu without a touched
+bucket may be present with k == 0. The DeviceAccumulator's is
+destructive like its read(), compacts on the device (csrc/gpu/compact.hip)
+and, as long as the layout did not change and nothing was handed over
+through _pending_arrays since the previous read_sparse, allocates no
+host array of total_buckets length.
+
 Bucket space: each (pid, code_object_id) gets a contiguous slot of
 ceil(load_size / 2^bucket_shift) buckets. The layout is rebuilt when new
 code objects appear (rare) — pending device state is flushed first.
@@ -217,6 +229,55 @@ class HostAccumulator:
                 s[:] = 0
         return out
 
+    def read_sparse(self, also_reset: bool = True) -> Dict[int, SparseRead]:
+        """gpu -> (buckets, hist, lanes, stalls) of the touched buckets:
+        the non-zero view of read_with_stalls (module docstring)."""
+        out = {}
+        for gpu in list(self._hists):
+            h, l = self._arrays(gpu)
+            nz = np.flatnonzero(h)
+            rows = np.zeros((len(nz), N_STALL_COLUMNS), dtype=np.uint64)
+            s = self._stalls.get(gpu)
+            if s is not None:
+                # The matrix grows lazily, so it may end before hist does.
+                have = nz < len(s)
+                rows[have] = s[nz[have]]
+            out[gpu] = (nz.astype(np.int64), h[nz], l[nz], rows)
+            if also_reset:
+                h[nz] = 0
+                l[nz] = 0
+                if s is not None:
+                    s[nz[have]] = 0
+        return out
+
+
+# read_sparse value: (buckets int64[k], hist u64[k], lanes u64[k],
+# stalls u64[k, N_STALL_COLUMNS]).
+SparseRead = Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]
+
+
+def _merge_sparse(chunks) -> SparseRead:
+    """Sum sparse chunks (buckets, hist, lanes, stalls-or-None) that may
+    share buckets into one ascending, duplicate-free SparseRead."""
+    if not chunks:
+        return (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.uint64),
+                np.zeros(0, dtype=np.uint64),
+                np.zeros((0, N_STALL_COLUMNS), dtype=np.uint64))
+    buckets, inverse = np.unique(
+        np.concatenate([c[0] for c in chunks]), return_inverse=True)
+    hist = np.zeros(len(buckets), dtype=np.uint64)
+    lanes = np.zeros(len(buckets), dtype=np.uint64)
+    stalls = np.zeros((len(buckets), N_STALL_COLUMNS), dtype=np.uint64)
+    at = 0
+    for b, h, l, s in chunks:
+        idx = inverse[at : at + len(b)]
+        at += len(b)
+        np.add.at(hist, idx, h)
+        np.add.at(lanes, idx, l)
+        if s is not None:
+            np.add.at(stalls, idx, s)
+    return buckets.astype(np.int64), hist, lanes, stalls
+
 
 def _grown_stalls(arr: Optional[np.ndarray], total: int) -> np.ndarray:
     """The stall matrix sized for the current layout, old rows kept (the
@@ -277,6 +338,10 @@ class DeviceAccumulator:
         # Bucketizers that were handed a flagged batch: only those hold a
         # device stall matrix worth reading back.
         self._flagged: set = set()
+        # gpu -> sparse chunks (global buckets, hist, lanes, stalls or
+        # None) drained from bucketizers by the sparse read: carry-over
+        # of a layout rebuild, consumed by whichever read comes next.
+        self._sparse: Dict[int, list] = {}
 
     def layout_changed(self) -> None:
         self._gen += 1
@@ -331,14 +396,47 @@ class DeviceAccumulator:
         self._fold_global(pid, gpu, h.astype(np.uint64),
                           l.astype(np.uint64), s)
 
+    def _drain_sparse(self, pid: int, gpu: int, b) -> None:
+        """Read-and-reset one bucketizer through the device compaction
+        into a sparse chunk in the global bucket space, using that pid's
+        current base/offset tables. O(touched buckets) on the host."""
+        local, h, l, s, overflow = b.read_sparse(True)
+        self.unknown_code_object += int(overflow[0])
+        self.out_of_range += int(overflow[1])
+        chunks = self._sparse.setdefault(gpu, [])
+        if len(local) == 0:
+            return
+        offs = self._local_offsets[pid]
+        slot = np.searchsorted(offs, local, side="right") - 1
+        buckets = (self._bases[pid][slot].astype(np.int64) +
+                   (local.astype(np.int64) - offs[slot].astype(np.int64)))
+        # Only a bucketizer that saw a flagged batch has stall counts.
+        stalls = s.astype(np.uint64) if (pid, gpu) in self._flagged else None
+        chunks.append((buckets, h.astype(np.uint64), l.astype(np.uint64),
+                       stalls))
+
+    def _fold_sparse(self, with_stalls: bool) -> None:
+        """Move the sparse chunks into the dense pending arrays, for the
+        dense reads. A chunk's buckets are unique (the local -> global
+        map is one to one), so plain indexed adds do."""
+        for gpu, chunks in self._sparse.items():
+            hist, lanes = self._pending_arrays(gpu)
+            for buckets, h, l, s in chunks:
+                hist[buckets] += h
+                lanes[buckets] += l
+                if with_stalls and s is not None:
+                    self._pending_stall_array(gpu)[buckets] += s
+        self._sparse.clear()
+
     def _bucketizer(self, pid: int, gpu: int):
         key = (pid, gpu)
         if self._layout_gen.get(key) != self._gen:
-            # Flush existing device state into the global pending arrays
-            # (with the OLD tables) before rebuilding for the new layout.
+            # Flush existing device state (with the OLD tables) before
+            # rebuilding for the new layout: kept as a sparse chunk, so
+            # a rebuild costs O(touched buckets) too.
             old = self._buckets.pop(key, None)
             if old is not None:
-                self._drain(pid, gpu, old, with_stalls=True)
+                self._drain_sparse(pid, gpu, old)
                 self._flagged.discard(key)
             slot_ids, local_offsets, global_base = \
                 self.layout.device_tables(pid)
@@ -381,6 +479,7 @@ class DeviceAccumulator:
         del also_reset
         for (pid, gpu), b in list(self._buckets.items()):
             self._drain(pid, gpu, b, with_stalls=False)
+        self._fold_sparse(with_stalls=False)
         self._pending_stalls.clear()
         out = {}
         for gpu in list(self._pending):
@@ -398,6 +497,7 @@ class DeviceAccumulator:
         del also_reset
         for (pid, gpu), b in list(self._buckets.items()):
             self._drain(pid, gpu, b, with_stalls=True)
+        self._fold_sparse(with_stalls=True)
         out = {}
         for gpu in list(self._pending):
             hist, lanes = self._pending_arrays(gpu)
@@ -406,6 +506,34 @@ class DeviceAccumulator:
             out[gpu] = (hist.copy(), lanes.copy(), stalls)
             hist[:] = 0
             lanes[:] = 0
+        return out
+
+    def read_sparse(self, also_reset: bool = True) -> Dict[int, SparseRead]:
+        """The touched buckets of read_with_stalls(), per gpu, compacted
+        on the device (module docstring). Destructive like read()."""
+        del also_reset
+        for (pid, gpu), b in list(self._buckets.items()):
+            self._drain_sparse(pid, gpu, b)
+        out = {}
+        for gpu in sorted(set(self._sparse) | set(self._pending)):
+            chunks = self._sparse.pop(gpu, [])
+            # Dense pending arrays exist only after a hand-over from the
+            # host accumulator: take what they hold and drop them, so the
+            # steady state keeps no total_buckets-sized host array.
+            pair = self._pending.pop(gpu, None)
+            stalls = self._pending_stalls.pop(gpu, None)
+            if pair is not None:
+                nz = np.flatnonzero(pair[0])
+                rows = None
+                if stalls is not None:
+                    rows = np.zeros((len(nz), N_STALL_COLUMNS),
+                                    dtype=np.uint64)
+                    have = nz < len(stalls)
+                    rows[have] = stalls[nz[have]]
+                chunks.append((nz.astype(np.int64), pair[0][nz],
+                               pair[1][nz], rows))
+            out[gpu] = _merge_sparse(chunks)
+        self._pending_stalls.clear()
         return out
 
     def drop_process(self, pid: int) -> None:

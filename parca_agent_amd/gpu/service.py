@@ -444,6 +444,16 @@ class GPUProfilerService:
         stream per source GPU (per-GPU fan-out for the daemon shape)."""
         if self.layout.total_buckets == 0:
             return
+        # Sparse read first: the accumulator hands over the touched
+        # buckets only (compacted on the device), so a flush costs
+        # O(touched buckets) whatever the layout's size.
+        if hasattr(self.accumulator, "read_sparse"):
+            for gpu, (buckets, hist, lane_hist, stalls) in sorted(
+                    self.accumulator.read_sparse(True).items()):
+                self._flush_pc_entries(
+                    gpu, buckets, hist, lane_hist,
+                    stalls if self.stall_reasons else None)
+            return
         if self.stall_reasons and hasattr(self.accumulator,
                                           "read_with_stalls"):
             for gpu, (hist, lane_hist, stalls) in sorted(
@@ -457,17 +467,31 @@ class GPUProfilerService:
     def _flush_pc_gpu(self, gpu: int, hist: np.ndarray,
                       lane_hist: np.ndarray,
                       stalls: Optional[np.ndarray] = None) -> None:
+        """Dense arrays over the bucket space: emit their non-zero
+        entries."""
         nonzero = np.nonzero(hist)[0]
-        if len(nonzero) == 0:
+        self._flush_pc_entries(
+            gpu, nonzero, hist[nonzero], lane_hist[nonzero],
+            stalls[nonzero] if stalls is not None else None)
+
+    def _flush_pc_entries(self, gpu: int, buckets: np.ndarray,
+                          counts: np.ndarray, lane_sums: np.ndarray,
+                          stall_rows: Optional[np.ndarray] = None) -> None:
+        """Emit one gpu's touched buckets: parallel arrays of ascending
+        global bucket index, sample count, active-lane sum and (optional)
+        stall row."""
+        if len(buckets) == 0:
             return
         offsets = self.layout.offsets()
+        slots = np.searchsorted(offsets, buckets, side="right") - 1
         now_ns = time.time_ns()
-        for bucket in nonzero:
-            slot = int(np.searchsorted(offsets, bucket, side="right")) - 1
+        for i in range(len(buckets)):
+            bucket = int(buckets[i])
+            slot = int(slots[i])
             pid, co_id = self.layout.key_of_slot(slot)
             info = self.code_objects.get(pid, co_id)
-            first, _ = self.layout.bucket_range(slot)
-            co_offset = (int(bucket) - first) << self.layout.bucket_shift
+            first = int(offsets[slot])
+            co_offset = (bucket - first) << self.layout.bucket_shift
             if info is not None:
                 mapping = info.mapping_file
                 address = info.vaddr_for_offset(co_offset)
@@ -483,18 +507,17 @@ class GPUProfilerService:
             # Wave-occupancy view: mean active lanes (of 64) at this PC,
             # from the exec-mask popcounts the bucketize kernel sums —
             # divergence shows up as avg_active_lanes << 64.
+            total = int(counts[i])
             labels = ()
-            if lane_hist[bucket] > 0:
-                avg_lanes = int(round(
-                    int(lane_hist[bucket]) / int(hist[bucket])))
+            if lane_sums[i] > 0:
+                avg_lanes = int(round(int(lane_sums[i]) / total))
                 labels = (("avg_active_lanes", str(avg_lanes)),)
             # Stall breakdown: one trace per non-zero stall column, plus
             # an unlabelled one for the samples that carried no issue
             # info; a bucket with an all-zero row stays one trace.
-            total = int(hist[bucket])
             parts = []
-            if stalls is not None:
-                row = stalls[bucket]
+            if stall_rows is not None:
+                row = stall_rows[i]
                 for col in np.nonzero(row)[0]:
                     parts.append((int(row[col]), labels + ((
                         "stall_reason", ev.STALL_COLUMN_NAMES[col]),)))
